@@ -2,20 +2,27 @@
 """bench.py — the driver's benchmark contract for ruserf_amd.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gossip|vivaldi|pushpull|churn]
+                    [--full] [--dump-outputs DIR]
 
 BASELINE.json's metric has two halves, "gossip node-rounds/sec (whole node) at 16M
-members; Vivaldi updates/sec".  The default run measures both in one invocation: the
-gossip leg is the line's `value`, the Vivaldi leg (configs[4], 64M members) is the
-line's `vivaldi` object with its own ms_per_step, roofline and cpu_baseline.
+members; Vivaldi updates/sec".  A plain run measures the headline only: it sets the
+gossip leg up, warms up, times --steps rounds and prints the line (`value`,
+`ms_per_step` = the milliseconds one timed round took).  `--full` measures both halves
+and everything beside them in one invocation: the gossip leg is the line's `value`, the
+Vivaldi leg (configs[4], 64M members) is the line's `vivaldi` object with its own
+ms_per_step, roofline and cpu_baseline, and the line carries the CPU baselines, the
+labelled gossip points and the configs[0] check.  `--dump-outputs DIR` writes what the
+timed path holds after its last timed step (a fixed, seeded sample of it) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 
 One step = one pass of the hot path over one batch of synthetic input:
   gossip  : one gossip round over the shard's members -> metric "node-rounds/s".
             Default 1M members per GPU (BASELINE configs[1] at N=1) in the reference's
             queue regime: the intent queue DEFAULT_QUEUE_DEPTH (8 704) deep, each member's
             QueueChecker pruning it to 4 096 every 150 rounds on its own phase inside the
-            timed rounds.  configs[2]'s 2M-per-GPU shard is `--members 2000000`; the line
-            also carries labelled points at 2M (the same regime) and with bounded 64-slot
-            queues (model points).
+            timed rounds.  configs[2]'s 2M-per-GPU shard is `--members 2000000`; with
+            `--full` the line also carries labelled points at 2M (the same regime) and
+            with bounded 64-slot queues (model points).
   vivaldi : one Vivaldi round (every member probes one neighbour and runs
             CoordinateClient::update) (configs[4]) -> "Vivaldi updates/s"
 Multi-GPU: one process per GPU (torch.distributed over RCCL), members sharded
@@ -42,6 +49,8 @@ SEED = 0x5EED5EED
 # writes self 88 + window slot 8 + window index 4 + filter sample 8 + filter meta 4  (D=8, W=20, F=3)
 VIVALDI_BYTES = 492
 HBM_PEAK_GBS = 8000.0
+# Vivaldi: HBM for the pre-generated probe inputs (64M members: 44 rounds at a time)
+PROBE_INPUT_BYTES = 32 << 30
 # the gossip headline runs the reference's queue regime: the intent queue deep enough that
 # nothing is dropped between QueueChecker ticks (4096 after a tick + ~24 a round x 150 rounds)
 DEFAULT_QUEUE_DEPTH = 8704
@@ -138,14 +147,26 @@ def run_vivaldi(args, rank, world):
         if refresher is not None:
             refresher.after_round(r, read_ptr[0])
 
-    # the probe inputs (peer id, observed rtt) of every round are generated up front by
-    # the synthetic network and are resident in HBM when the timed region starts
+    # the probe inputs (peer id, observed rtt) of a round are generated by the synthetic
+    # network before the round is timed and are resident in HBM when it runs.  All rounds
+    # up front when they fit PROBE_INPUT_BYTES (12 B per member and round); a longer run is
+    # timed in segments of K rounds, the next K rounds' inputs generated between them, outside
+    # the timed time.  The inputs of round r depend on r and the seed only, so the rounds
+    # compute the same either way.
     rounds = args.warmup + args.steps
-    peer = torch.empty((rounds, per), dtype=torch.int32, device="cuda")
-    rtt = torch.empty((rounds, per), dtype=torch.int64, device="cuda")
-    for r in range(rounds):
-        g.gen_probes(r, peer[r].data_ptr(), rtt[r].data_ptr())
-    step = [0]
+    K = args.probe_rounds or max(1, PROBE_INPUT_BYTES // (12 * per))
+    slots = min(rounds, K + 1)  # a segment's K rounds and the round after them (presend)
+    peer = torch.empty((slots, per), dtype=torch.int32, device="cuda")
+    rtt = torch.empty((slots, per), dtype=torch.int64, device="cuda")
+    resident = [0]  # rounds [0, resident) have been generated
+
+    def top_up(b):
+        """before a segment that starts at round b: rounds b .. b + K resident (the rounds
+        before b are done, so their slots are free)"""
+        upto = min(rounds, b + K + 1)
+        for r in range(resident[0], upto):
+            g.gen_probes(r, peer[r % slots].data_ptr(), rtt[r % slots].data_ptr())
+        resident[0] = max(resident[0], upto)
 
     read_ptr = [None]  # the table a round reads (the other one after it)
 
@@ -154,42 +175,47 @@ def run_vivaldi(args, rank, world):
     def observe(r):
         read_ptr[0] = g.table_ptr()[0]
         if chunks > 1:  # the exchange of chunk i + 1 beside the observe of chunk i (round_chunked)
-            sv.round_chunked(r, peer[r].data_ptr(), rtt[r].data_ptr(), chunks=chunks)
+            sv.round_chunked(r, peer[r % slots].data_ptr(), rtt[r % slots].data_ptr(), chunks=chunks)
         else:
-            g.observe(r % 16, peer[r].data_ptr(), rtt[r].data_ptr(), None, r)
+            g.observe(r % 16, peer[r % slots].data_ptr(), rtt[r % slots].data_ptr(), None, r)
 
     def fetch(r):
         if targeted and chunks == 1:
-            sv.fetch(peer[r].data_ptr())
+            sv.fetch(peer[r % slots].data_ptr())
 
     def presend(r):
         # round r + 1's requests go out while round r's observe runs
         if targeted and chunks == 1 and r + 1 < rounds:
-            sv.presend(peer[r + 1].data_ptr())
+            sv.presend(peer[(r + 1) % slots].data_ptr())
 
-    for _ in range(args.warmup):
-        fetch(step[0])
-        observe(step[0])
-        presend(step[0])
-        refresh(step[0])
-        step[0] += 1
-    torch.cuda.synchronize()
-    barrier(world)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    kernel_ms = []
-    for i in range(args.steps):
-        fetch(step[0])
-        evs[i][0].record(stream)
-        observe(step[0])
-        evs[i][1].record(stream)
-        presend(step[0])
-        refresh(step[0])
-        step[0] += 1
-    torch.cuda.synchronize()
-    barrier(world)
-    wall = time.perf_counter() - t0
+
+    def run_rounds(first, last, timed):
+        """rounds [first, last) in segments of at most K; returns the seconds spent in them"""
+        spent, b = 0.0, first
+        while b < last:
+            e = min(last, b + K)
+            top_up(b)
+            torch.cuda.synchronize()
+            barrier(world)
+            t0 = time.perf_counter()
+            for r in range(b, e):
+                fetch(r)
+                if timed:
+                    evs[r - first][0].record(stream)
+                observe(r)
+                if timed:
+                    evs[r - first][1].record(stream)
+                presend(r)
+                refresh(r)
+            torch.cuda.synchronize()
+            barrier(world)
+            spent += time.perf_counter() - t0
+            b = e
+        return spent
+
+    run_rounds(0, args.warmup, False)
+    wall = run_rounds(args.warmup, rounds, True)
     kernel_ms = [a.elapsed_time(b) for a, b in evs]
     if chunks > 1:  # the observe kernels' own time: the chunks' launches summed per round
         kernel_ms = [sum(a.elapsed_time(b) for a, b in rnd) for rnd in sv.chunk_events[-args.steps:]]
@@ -200,6 +226,8 @@ def run_vivaldi(args, rank, world):
     updates = per * world * args.steps
     value = updates / wall
     achieved = VIVALDI_BYTES * per / avg_kernel_s / 1e9
+    if args.dump_outputs and world == 1:
+        dump_vivaldi_outputs(g, args.dump_outputs)
     g.close()
     return {
         "metric": "Vivaldi updates/s", "value": value, "unit": "updates/s",
@@ -220,6 +248,19 @@ def run_vivaldi(args, rank, world):
         # --members is per GPU unless --members-total; the default keeps 64M members in total
         "scaling": "strong" if args.members_total else "weak",
     }
+
+
+def dump_vivaldi_outputs(g, out_dir, blocks=64, block_rows=1024):
+    """--dump-outputs: the coordinate table after the last timed round, as get_rows returns it
+    (float64).  The table is too large to write whole, so a fixed sample: `blocks` runs of
+    `block_rows` consecutive members at seeded offsets, the same for every run of the same size."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.Generator(np.random.Philox(SEED + 7))
+    block_rows = min(block_rows, g.n)
+    first = np.sort(rng.integers(0, g.n - block_rows + 1, size=blocks))
+    rows = np.concatenate([g.get_rows(int(f), block_rows) for f in first])
+    np.save(os.path.join(out_dir, "vivaldi_first_members.npy"), first.astype(np.float64))
+    np.save(os.path.join(out_dir, "vivaldi_rows.npy"), rows)
 
 
 def cpu_baseline_vivaldi(seconds_target=8.0):
@@ -250,7 +291,7 @@ def model_point(args, rank, world, members):
     from bench_gossip import run_gossip
     a = argparse.Namespace(**vars(args))
     a.members, a.queue_cap, a.settle = members, 64, None
-    a.queue_depth, a.check_every = 0, 0
+    a.queue_depth, a.check_every, a.dump_outputs = 0, 0, None
     torch.cuda.empty_cache()
     r = run_gossip(a, rank, world)
     keep = ["value", "unit", "ms_per_step", "merges_per_s", "records_per_round_per_gpu", "queue_pruned_per_round",
@@ -269,7 +310,7 @@ def regime_point(args, rank, world, members):
     same box, same call: a labelled point beside the configs[1] headline."""
     from bench_gossip import run_gossip
     a = argparse.Namespace(**vars(args))
-    a.members = members
+    a.members, a.dump_outputs = members, None
     torch.cuda.empty_cache()
     r = run_gossip(a, rank, world)
     keep = ["value", "unit", "ms_per_step", "merges_per_s", "records_per_round_per_gpu", "queue_pruned_per_round",
@@ -385,7 +426,21 @@ def main():
     ap.add_argument("--vivaldi-chunks", type=int, default=4,
                     help="vivaldi, N>1, targeted: the round pipelined in this many member chunks (chunk i observed "
                          "while chunk i+1's rows are exchanged); 1: the exchange before the whole observe")
+    ap.add_argument("--probe-rounds", type=int, default=None,
+                    help="vivaldi: rounds of probe inputs resident in HBM at a time; a longer run is timed in "
+                         "segments of this many rounds (default: what fits 32 GiB, all rounds of a short run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU baselines, the labelled gossip "
+                         "points (2M members, 64-slot queues) and the Vivaldi leg with its configs[0] check; "
+                         "--no-cpu-baseline, --no-extra-points and --no-vivaldi take parts of it away again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path holds after its last step as "
+                         "DIR/<name>.npy (float32 / float64; a fixed seeded sample of the large tables)")
     args = ap.parse_args()
+    if args.probe_rounds is not None and args.probe_rounds < 1:
+        ap.error("--probe-rounds must be at least 1")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_extra_points = args.no_vivaldi = True
     if args.queue_depth is None:
         args.queue_depth = DEFAULT_QUEUE_DEPTH if args.queue_cap <= 64 else 0
     if args.check_every is None:

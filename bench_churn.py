@@ -102,6 +102,9 @@ def run_churn(args, rank, world):
                   "expired_total": int(eng.expired().astype(np.uint64).sum()),
                   "deferred_per_round_by_class": dict(zip(["tiny", "small", "middle", "full"],
                                                           (eng.deep_class_stats() / max(1, timed_rounds)).tolist()))}
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        from bench_gossip import dump_engine_outputs
+        dump_engine_outputs(eng, args.dump_outputs)
     eng.close()
     if world > 1:  # independent replicas (configs[3] is a one-GPU cluster)
         t_ = torch.tensor([wall], dtype=torch.float64, device="cuda")

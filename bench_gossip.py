@@ -74,6 +74,54 @@ def kernel_bytes(qcap, senders, records, fanout=3):
     return emit, merge_s8d, merge_ext
 
 
+DUMP_MEMBERS = 65536       # --dump-outputs: members sampled for the per-member arrays
+DUMP_VIEW_BYTES = 16 << 20   # ... bytes of view rows (whole rows of sampled members)
+DUMP_QUEUE_BYTES = 8 << 20   # ... bytes of queue rows (every slot of sampled members' three queues)
+
+
+def dump_engine_outputs(eng, out_dir, prefix=""):
+    """--dump-outputs: what the engine holds after the last timed round, as a caller reads it
+    through the inspection calls, written as out_dir/<prefix><name>.npy.  The shard is too large
+    to write whole, so a fixed sample (seeded, the same for every run of the same size): the
+    per-member state of DUMP_MEMBERS members, and the whole view rows and queues of the first
+    few of them.  Every value is an integer below 2^53 or a u8 / u16, exact in float64 /
+    float32; the 64-bit digests are split into two 32-bit halves."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, s = eng.n_loc, eng.cfg.n_subjects
+    rng = np.random.Generator(np.random.Philox(SEED + 7))
+    picked = rng.choice(n, size=min(n, DUMP_MEMBERS), replace=False).astype(np.int64)
+    ids = np.sort(picked)
+    out = {"member_ids": ids.astype(np.float64)}
+    m = eng.members()
+    for k in ("clock", "event_clock", "query_clock"):
+        out[k] = m[k][ids].astype(np.float64)
+    out["digest_lo"] = (m["digest"][ids] & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    out["digest_hi"] = (m["digest"][ids] >> np.uint64(32)).astype(np.float64)
+    out["err"] = m["err"][ids].astype(np.float64)
+    out["serf_state"] = m["serf_state"][ids].astype(np.float32)
+    out["queue_lengths"] = eng.queue_lengths()[ids].astype(np.float64)
+    out["pruned"] = eng.pruned()[ids].astype(np.float64)
+    out["expired"] = eng.expired()[ids].astype(np.float64)
+    out["merged_total"] = np.array([eng.merged_total()], dtype=np.float64)
+    # whole view rows: ltime f64 + time f64 + status f32 + kind f32 = 24 B per entry
+    rows = np.sort(picked[:max(1, min(64, len(picked), DUMP_VIEW_BYTES // (24 * s)))])
+    lt, st, kd, tm = (np.stack(x) for x in zip(*(eng.view(with_time=True, rows=(int(r), 1)) for r in rows)))
+    out["view_rows"] = rows.astype(np.float64)
+    out["view_ltime"], out["view_time"] = lt.astype(np.float64), tm.astype(np.float64)
+    out["view_status"], out["view_kind"] = st.astype(np.float32), kd.astype(np.float32)
+    # whole queues (intent, query, event; every slot, in send order): rumor f64 + seq f64 +
+    # transmits f32 + len f32 = 24 B per slot
+    width = max(eng.cfg.depths())
+    rows = np.sort(picked[:max(1, min(8, len(picked), DUMP_QUEUE_BYTES // (24 * 3 * width)))])
+    qr, qs, qt, ql = (np.concatenate(x) for x in zip(*(eng.queues_rows(int(r), 1, width) for r in rows)))
+    out["queue_rows"] = rows.astype(np.float64)
+    out["queue_rumor"], out["queue_seq"] = qr.astype(np.float64), qs.astype(np.float64)
+    out["queue_transmits"], out["queue_len"] = qt.astype(np.float32), ql.astype(np.float32)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), a)
+
+
 def run_gossip(args, rank, world):
     from ruserf_amd import workload as W
     from ruserf_amd.dist import ShardedGossip
@@ -203,6 +251,8 @@ def run_gossip(args, rank, world):
     else:
         merged_all, err_all, pruned_all, qpm_all = float(merged), float(err_members), float(pruned), \
             float(qprune_members)
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_engine_outputs(eng, args.dump_outputs)
     eng.close()  # free the shard's HBM before bench.py's next leg
     node_rounds = n * args.steps
     avg = [x / max(1, nr) for x in phase_ms]  # ms per round per phase

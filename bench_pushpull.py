@@ -107,6 +107,9 @@ def run_pushpull(args, rank, world):
     # and event-buffer rows read (writes are the few changed entries)
     per_pair = sb + cfg.n_subjects * 16 + cfg.event_buffer_size * (12 + 8 * cfg.slot_k)
     achieved = per_pair * pairs_per_launch / (avg_ms / 1e3) / 1e9
+    if getattr(args, "dump_outputs", None):
+        from bench_gossip import dump_engine_outputs
+        dump_engine_outputs(eng, args.dump_outputs)
     eng.close()
     merges = n * args.steps
     return {
