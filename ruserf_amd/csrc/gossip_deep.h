@@ -1,4 +1,4 @@
-// gossip_deep.h — deep transmit-limited queues: the whole-queue paths (included by gossip.hip).
+// gossip_deep.h — deep transmit-limited queues: the whole-queue paths (the round unit's: gossip.hip).
 //
 // A deep queue (queue_depth > queue_cap) is its sorted register head (the q_* slots emission
 // works on) plus an UNORDERED tail in HBM with a summary {count, length bound, key bound}.  The
@@ -11,6 +11,9 @@
 // member's emission with every item of its queues in LDS.  The block routines first in this file
 // run the QueueChecker's prune (check_stream_kernel).
 #pragma once
+#include "gossip_ctx.h"
+#include "gossip_diag.h"
+#include "gossip_queue4.h"
 
 namespace {
 

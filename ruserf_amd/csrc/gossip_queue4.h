@@ -1,6 +1,6 @@
 // gossip_queue4.h — transmit-limited queues of 65..256 slots (queue_cap up to 256; the
-// reference's max_queue_depth is 4096, core/src/options.rs:249).  Included by gossip.hip
-// after the one-slot-per-lane queue functions, whose invariants these keep exactly:
+// reference's max_queue_depth is 4096, core/src/options.rs:249).  Built on the
+// one-slot-per-lane queue functions (gossip_queue.h), whose invariants these keep exactly:
 //   * a queue is SORTED in send order by the key (transmits, ~len, ~seq), live items first;
 //   * get_broadcasts picks the leading run that fits the byte budget, then offers what is
 //     left to later (shorter) items one by one, bumps the picks (or retires them at the
@@ -12,6 +12,9 @@
 // totals).  Re-orderings go through the wave's 256-entry LDS row (QLds4): every item is
 // written to its new slot and read back in blocked order.
 #pragma once
+#include "gossip_queue.h"
+
+namespace {
 
 constexpr uint32_t kQK = 4;              // slots per lane
 constexpr uint32_t kQ4Cap = kWave * kQK;  // 256
@@ -499,3 +502,14 @@ __device__ __forceinline__ uint32_t q4_expire(const GCfg& c, Q4& Q, uint32_t lan
   else q4_scatter<false>(c, Q, lane, dst, n_keep, row);
   return n_stale;
 }
+
+// a member's pending list applied to queues of either layout (qcap <= 64: one slot per
+// lane; up to 256: four, gossip_queue4.h); `row` is a QLds4 (which holds a QLds)
+__device__ __forceinline__ uint32_t pend_flush_any(const GCfg& c, const GState& s, uint64_t l, uint32_t lane,
+                                                   uint32_t pc, QLds4& row) {
+  if (c.qcap > kWave) return q4_pend_flush_wave(c, s, l, lane, pc, row);
+  return pend_flush_wave(c, s, l, lane, pc, *reinterpret_cast<QLds*>(&row));
+}
+static_assert(sizeof(QLds4) >= sizeof(QLds), "a QLds4 row holds a QLds");
+
+}  // namespace
