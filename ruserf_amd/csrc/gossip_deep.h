@@ -1627,10 +1627,11 @@ __global__ void __launch_bounds__(kDeepBlkThreads) emit_deep_block_kernel(
 }
 
 // ---- the QueueChecker's prune (check_stream_kernel) --------------------------------------
-// One block per listed (member, queue).  Pass 1 streams head and tail once and keeps only the
-// 8-B keys in LDS (live head keys first, then the tail's in index order); one select over the
-// LDS keys finds the max-th key; pass 2 streams the tail again and compacts it in place.  Two
-// blocks per CU (the keys of a full queue are 70 KB).
+// One block per listed (member, queue).  The intent queue's packed 8-B items are read once and
+// stay in LDS (live head items first, then the tail's in index order): the select derives its
+// keys from them and pass 2 writes the kept ones back (check_prune_packed).  The 16-B queues
+// keep only the 8-B keys in LDS; one select over them finds the max-th key and pass 2 streams
+// the tail again and compacts it in place.  Two blocks per CU (a full queue is 70 KB either way).
 #ifndef RSF_CHK_U1
 #define RSF_CHK_U1 32  // check_stream_kernel's pass 1: 16-B loads in flight per thread (16: 99.2 ms per 1M-member tick, 32: 97.3)
 #endif
@@ -1638,10 +1639,17 @@ __global__ void __launch_bounds__(kDeepBlkThreads) emit_deep_block_kernel(
 #define RSF_CHK_U2 16  // its pass 2 (the compaction): items per thread per batch
 #endif
 constexpr uint32_t kChkU2 = RSF_CHK_U2;
+constexpr uint32_t kChkDigit = 10;  // the packed path's radix digit (a 4 KB histogram: two blocks per CU still)
+constexpr uint32_t kChkUL = 4;      // its LDS scans: items per thread in flight
 struct CheckLds {
-  uint32_t hist[3][256];
+  union {
+    uint32_t hist[3][256];            // lds_select3's (the 16-B queues)
+    uint32_t wide[1u << kChkDigit];   // the packed path's
+  };
   uint64_t w64[kDeepWaves], w64b[kDeepWaves];
   uint32_t wcnt[kChkU2][kDeepWaves];
+  uint32_t txh[64];  // the packed path: items per transmit count
+  uint32_t pw[2][kDeepWaves];  // its per-wave counts
   uint32_t sel_digit[3], sel_need[3], nb, hn;
 };
 
@@ -1751,9 +1759,258 @@ __device__ void lds_select3(const uint64_t* __restrict__ keys, uint32_t n, Check
   for (int j = 0; j < 3; ++j) out[j] = prefix[j];
 }
 
+#if RSF_DEEP_PROF
+#define RSF_CK(i) ck[i] = clock64()
+#else
+#define RSF_CK(i)
+#endif
+
+// ---- the packed intent queue's prune: the items themselves in LDS ------------------------
+// A packed item is as wide as a key, and its place in the queue's order follows from its own
+// fields and the queue's next seq: transmits, then 63 - length, then age = (next seq - seq) mod
+// 2^25.  That is monotone in tlq_key -- every queued item is older than next seq, and an age of
+// 2^24 is flagged long before the window could alias -- so the select and every test against
+// its result use this compact form, the head's items (packed the same way) included.
+__device__ __forceinline__ uint32_t pk_tx(uint64_t x) { return (uint32_t)(x >> 25) & 0x3F; }
+// below the transmits (31 bits): 63 - length over age
+__device__ __forceinline__ uint32_t pk_sub(uint64_t x, uint32_t nseq) {
+  return ((0x3Fu - ((uint32_t)(x >> 31) & 0x3F)) << 25) | ((nseq - (uint32_t)x) & kTailSeqMask);
+}
+// the same without the leading bits of either field that every item of the queue shares (from
+// the AND / OR of pass 1): typically 1 bit of length over 13-15 of age, two 10-bit digits
+struct PkFold {
+  uint32_t wa, ml, ma;  // age bits kept, the length's mask, the age's mask
+};
+__device__ __forceinline__ uint32_t pk_fold(uint32_t sub, const PkFold& f) {
+  return (((sub >> 25) & f.ml) << f.wa) | (sub & f.ma);
+}
+__device__ __forceinline__ uint64_t pk_key(uint64_t x, uint32_t nseq, const PkFold& f) {
+  return ((uint64_t)pk_tx(x) << 31) | pk_fold(pk_sub(x, nseq), f);
+}
+
+// check_stream_kernel's work on one intent queue (q = 0) over its max; returns the items it
+// held, 0 if it left the queue alone:
+//   pass 1 streams the tail once into LDS (the live head items first, packed), with the AND /
+//          OR of the sub keys and the items per transmit count (per-thread counters, no atomics, for
+//          the counts 0..3 that hold nearly every item);
+//   the select takes the transmit count holding the keep-th key from those counts, then 10-bit
+//          digits of the folded sub key over that count's items alone;
+//   pass 2 writes the kept items (key <= T) from LDS over the tail in index order -- each wave
+//          a contiguous run of the tail, its place from one count pass and a block sum -- so a
+//          sealed prefix stays a prefix; nothing is read from the tail again.
+__device__ __forceinline__ uint32_t check_prune_packed(const GCfg& c, const GState& s, uint64_t l, uint32_t keep, uint32_t tc,
+                                                       uint64_t* __restrict__ items, CheckLds& d, uint64_t* ck) {
+  static_assert((1u << kChkDigit) == 4 * kDeepThreads, "the digit search reads four bins per thread");
+  const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
+  const uint64_t hb = l * 3 * c.qcap;
+  uint64_t* const t8 = tail8(s, c, l);
+  const uint32_t nseq = s.q_next_seq[l * 3];  // (every queued item is older)
+  if (tid < 64) d.txh[tid] = 0;
+  __syncthreads();
+  // per thread: AND / OR of the sub keys and the items per transmit count -- counts 0..3 (nearly
+  // every item) in the four bytes of one word (a thread sees at most 35 items), the rest (a
+  // handful in a settled queue) by an atomic each
+  uint32_t an = ~0u, orr = 0, c4 = 0;
+  auto count = [&](bool in, uint32_t tx) {
+    c4 += in && tx < 4 ? 1u << (8 * tx) : 0u;
+    if (in && tx >= 4) atomicAdd(&d.txh[tx], 1u);
+  };
+  if (w == 0) {
+    const bool live_h = lane < c.qcap && s.q_rumor[hb + lane] != kEmpty;
+    const uint64_t lm = ballot(live_h);
+    if (live_h) {
+      const uint64_t x = tail_pack(c, s.q_rumor[hb + lane], s.q_seq[hb + lane], s.q_txlen[hb + lane]);
+      items[mbcnt(lm)] = x;
+      an = orr = pk_sub(x, nseq);
+      count(true, pk_tx(x));
+    }
+    if (lane == 0) d.hn = (uint32_t)__popcll(lm);
+  }
+  __syncthreads();
+  const uint32_t hn = d.hn, n = hn + tc;
+  uint64_t* const ti = items + hn;
+  constexpr uint32_t U1 = RSF_CHK_U1;
+  uint32_t t_or = 0;  // the tail's own OR: an item near the end of the packed seq window shows in it
+  for (uint32_t b = 0; b < tc; b += U1 * kDeepThreads) {
+    // (a lane past the end reads the last item again: the AND / OR do not change, and it is
+    // neither stored nor counted)
+    uint64_t x[U1];
+#pragma unroll
+    for (uint32_t u = 0; u < U1; ++u) {
+      const uint32_t i = b + u * kDeepThreads + tid;
+      x[u] = t8[i < tc ? i : tc - 1];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < U1; ++u) {
+      const uint32_t i = b + u * kDeepThreads + tid;
+      const uint32_t sub = pk_sub(x[u], nseq);
+      if (i < tc) ti[i] = x[u];
+      an &= sub;
+      t_or |= sub;
+      count(i < tc, pk_tx(x[u]));
+    }
+  }
+  if (t_or & kTailAgeFlag) atomicOr(s.err + l, (uint32_t)RSF_E_DEEP_INVARIANT);
+  orr |= t_or;
+  const uint64_t ao = wave_or_u64(((uint64_t)orr << 32) | (uint32_t)~an);  // (AND as the OR of the complements)
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t sum = wave_inclusive_sum_u32((c4 >> (8 * k)) & 0xFF);
+    if (lane == kWave - 1 && sum) atomicAdd(&d.txh[k], sum);
+  }
+  if (lane == 0) d.w64[w] = ao;
+  __syncthreads();
+  if (n <= keep) return 0;  // (listed by the same count: cannot happen)
+#pragma unroll
+  for (uint32_t v = 0; v < kDeepWaves; ++v) {
+    an &= ~(uint32_t)d.w64[v];
+    orr |= (uint32_t)(d.w64[v] >> 32);
+  }
+  RSF_CK(1);
+  const uint32_t var = an ^ orr, wl = 32u - (uint32_t)__clz((int)(var >> 25));
+  PkFold f;
+  f.wa = 32u - (uint32_t)__clz((int)(var & kTailSeqMask));
+  f.ml = (1u << wl) - 1;
+  f.ma = (1u << f.wa) - 1;
+  // the largest key kept
+  const bool any = keep > 0;
+  uint64_t T = 0ull;
+  if (any) {
+    if (w == 0) {  // the transmit count holding it
+      const uint32_t h = d.txh[lane], incl = wave_inclusive_sum_u32(h), excl = incl - h;
+      if (excl < keep && keep <= incl) {
+        d.sel_digit[0] = lane;
+        d.sel_need[0] = keep - excl;
+      }
+    }
+    __syncthreads();
+    const uint32_t cs = d.sel_digit[0];
+    uint32_t need = d.sel_need[0], pre = 0;
+    const uint32_t W = wl + f.wa;
+    for (uint32_t hi = W; hi > 0;) {  // the folded sub key's bits [lo, hi) of that count's items under the prefix
+      const uint32_t lo = hi > kChkDigit ? hi - kChkDigit : 0u, dm = (1u << (hi - lo)) - 1;
+      for (uint32_t i = tid; i < (1u << kChkDigit); i += kDeepThreads) d.wide[i] = 0;
+      __syncthreads();
+      for (uint32_t i0 = 0; i0 < n; i0 += kChkUL * kDeepThreads) {
+        uint64_t x[kChkUL];
+#pragma unroll
+        for (uint32_t u = 0; u < kChkUL; ++u) {
+          const uint32_t i = i0 + u * kDeepThreads + tid;
+          x[u] = items[i < n ? i : 0u];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kChkUL; ++u) {
+          const uint32_t i = i0 + u * kDeepThreads + tid;
+          const uint32_t k = pk_fold(pk_sub(x[u], nseq), f);
+          if (i < n && pk_tx(x[u]) == cs && (hi == W || (k >> hi) == pre)) atomicAdd(&d.wide[(k >> lo) & dm], 1u);
+        }
+      }
+      __syncthreads();
+      {  // the bin holding the need-th: four bins per thread, a block-wide running count
+        const uint32_t h0 = d.wide[4 * tid], h1 = d.wide[4 * tid + 1], h2 = d.wide[4 * tid + 2], h3 = d.wide[4 * tid + 3];
+        const uint32_t sum = h0 + h1 + h2 + h3, incl = wave_inclusive_sum_u32(sum);
+        if (lane == kWave - 1) d.pw[0][w] = incl;
+        __syncthreads();
+        uint32_t acc = incl - sum;
+#pragma unroll
+        for (uint32_t v = 0; v < kDeepWaves; ++v) acc += v < w ? d.pw[0][v] : 0u;
+        if (acc < need && need <= acc + sum) {
+          uint32_t b = 0;
+          if (acc + h0 < need) {
+            acc += h0;
+            b = 1;
+            if (acc + h1 < need) {
+              acc += h1;
+              b = 2;
+              if (acc + h2 < need) {
+                acc += h2;
+                b = 3;
+              }
+            }
+          }
+          d.sel_digit[0] = 4 * tid + b;
+          d.sel_need[0] = need - acc;
+        }
+      }
+      __syncthreads();
+      pre = (pre << (hi - lo)) | d.sel_digit[0];
+      need = d.sel_need[0];
+      hi = lo;
+    }
+    T = ((uint64_t)cs << 31) | pre;
+  }
+  RSF_CK(2);
+  // pass 2: wave w owns the tail's items [lo, hi); its kept items go to the tail at the count of
+  // kept items before them
+  const uint32_t m = min(s.tseal[l * 3].x, tc);
+  const uint32_t seg = ((tc + kDeepWaves - 1) / kDeepWaves + kWave - 1) & ~(kWave - 1);
+  const uint32_t lo = min(w * seg, tc), hi = min(lo + seg, tc);
+  uint32_t cnt = 0, cnt_sealed = 0;
+  for (uint32_t b = lo; b < hi; b += kChkUL * kWave) {
+    uint64_t x[kChkUL];
+#pragma unroll
+    for (uint32_t u = 0; u < kChkUL; ++u) {
+      const uint32_t i = b + u * kWave + lane;
+      x[u] = ti[i < hi ? i : lo];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kChkUL; ++u) {
+      const uint32_t i = b + u * kWave + lane;
+      const bool kp = any && i < hi && pk_key(x[u], nseq, f) <= T;
+      cnt += (uint32_t)__popcll(ballot(kp));
+      cnt_sealed += (uint32_t)__popcll(ballot(kp && i < m));
+    }
+  }
+  if (lane == 0) {
+    d.pw[0][w] = cnt;
+    d.pw[1][w] = cnt_sealed;
+  }
+  __syncthreads();
+  uint32_t at = 0, tot = 0, ms = 0;
+#pragma unroll
+  for (uint32_t v = 0; v < kDeepWaves; ++v) {
+    at += v < w ? d.pw[0][v] : 0u;
+    tot += d.pw[0][v];
+    ms += d.pw[1][v];
+  }
+  for (uint32_t b = lo; b < hi; b += kChkUL * kWave) {
+    uint64_t x[kChkUL];
+#pragma unroll
+    for (uint32_t u = 0; u < kChkUL; ++u) {
+      const uint32_t i = b + u * kWave + lane;
+      x[u] = ti[i < hi ? i : lo];
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kChkUL; ++u) {
+      const uint32_t i = b + u * kWave + lane;
+      const bool kp = any && i < hi && pk_key(x[u], nseq, f) <= T;
+      const uint64_t km = ballot(kp);
+      if (kp) t8[at + mbcnt(km)] = x[u];
+      at += (uint32_t)__popcll(km);
+    }
+  }
+  RSF_CK(3);
+  // the head is sorted: the items past T are a suffix of its slots
+  if (tid < c.qcap && s.q_rumor[hb + tid] != kEmpty &&
+      (!any || pk_key(tail_pack(c, 0u, s.q_seq[hb + tid], s.q_txlen[hb + tid]), nseq, f) > T)) {
+    s.q_rumor[hb + tid] = kEmpty;
+    s.q_seq[hb + tid] = 0;
+    s.q_txlen[hb + tid] = 0;
+  }
+  if (tid == 0) {
+    const uint4 old = s.tsum[l * 3], os = s.tseal[l * 3];
+    // the bounds stay valid lower bounds (only items left)
+    s.tsum[l * 3] = tot ? make_uint4(tot, old.y, old.z, old.w) : kTSumEmpty;
+    s.tseal[l * 3] = ms ? make_uint4(ms, os.y, os.z, os.w) : kTSumEmpty;
+  }
+  __syncthreads();  // (the LDS items are free for the next queue)
+  return n;
+}
+
 // QueueChecker prune of the deep queues check_queues_kernel listed (entries l * 3 + q): keep the
 // `max` smallest keys of head and tail (each member's own max with qmax) and drop the rest.
-// One 256-thread block per (member, queue):
+// The intent queue's packed items: check_prune_packed above.  The 16-B queues, in this kernel's
+// body, one 256-thread block per (member, queue):
 //   pass 1 streams the head and the tail once and keeps only their 8-B keys in LDS (plus, with
 //          transmit counts below 256, the histogram of the keys' first varying byte);
 //   one radix select over the LDS keys finds the max-th smallest key T;
@@ -1770,10 +2027,16 @@ __global__ void __launch_bounds__(kDeepThreads) check_stream_kernel(GCfg c, GSta
   __shared__ uint64_t keys[kDeepItems];
   const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
 #if RSF_DEEP_PROF
-  uint64_t pf[5] = {0, 0, 0, 0, 0}, pc = 0;
-#define RSF_CK(i) const uint64_t ck##i = clock64()
+  uint64_t pf[5] = {0, 0, 0, 0, 0}, pc = 0, ck[5];
+  auto tally = [&](uint32_t n) {  // a pruned queue's clocks: pass 1 / select / pass 2 / rest, and its items
+    ck[4] = clock64();
+    for (int i = 0; i < 4; ++i) pf[i] += ck[i + 1] - ck[i];
+    pf[4] += n;
+    pc++;
+  };
 #else
-#define RSF_CK(i)
+  uint64_t* const ck = nullptr;
+  auto tally = [](uint32_t) {};
 #endif
   // check_queues_kernel's entries at fixed places, kEmpty for a queue under its max; the next
   // entry is read while this one is worked on
@@ -1792,10 +2055,12 @@ __global__ void __launch_bounds__(kDeepThreads) check_stream_kernel(GCfg c, GSta
       if (tid == 0) atomicOr(s.err + l, (uint32_t)RSF_E_DEEP_INVARIANT);
       continue;
     }
-    // the intent queue's packed items (q == 0) or the 16-B items of the others
-    uint4* const t = q ? tail16(s, q) + l * tstride_of(c, q) : nullptr;
-    uint64_t* const t8 = q ? nullptr : tail8(s, c, l);
-    const uint32_t nseq = s.q_next_seq[l * 3 + q];  // (every tail item is older)
+    if (q == 0) {  // the intent queue's packed items
+      const uint32_t np = check_prune_packed(c, s, l, keep, tc, keys, d, ck);
+      if (np) tally(np);
+      continue;
+    }
+    uint4* const t = tail16(s, q) + l * tstride_of(c, q);  // the 16-B items of the others
     // pass 1: the keys into LDS, AND / OR of them, and (transmit counts below 256: byte 7 is
     // zero in every key) the histogram of byte 6 -- the first radix pass of the selects
     const bool fuse = c.tx_limit < 256;
@@ -1836,37 +2101,17 @@ __global__ void __launch_bounds__(kDeepThreads) check_stream_kernel(GCfg c, GSta
         }
       }
     };
-    if (t8) {
-      bool old_item = false;  // an item near the end of the packed seq window
-      for (uint32_t b = 0; b < tc; b += U1 * kDeepThreads) {
-        uint64_t x[U1];
+    for (uint32_t b = 0; b < tc; b += U1 * kDeepThreads) {
+      uint4 x[U1];
 #pragma unroll
-        for (uint32_t u = 0; u < U1; ++u) {
-          const uint32_t i = b + u * kDeepThreads + tid;
-          x[u] = i < tc ? t8[i] : 0ull;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U1; ++u) {
-          const uint32_t i = b + u * kDeepThreads + tid;
-          const uint32_t tl = tail_tl(x[u]);
-          old_item |= i < tc && tail_age_over(x[u], nseq);
-          put(i, i < tc, tlq_key(tl & 0xFFFF, tl >> 16, tail_seq(x[u], nseq)));
-        }
+      for (uint32_t u = 0; u < U1; ++u) {
+        const uint32_t i = b + u * kDeepThreads + tid;
+        x[u] = i < tc ? t[i] : make_uint4(0, 0, 0, 0);
       }
-      if (old_item) atomicOr(s.err + l, (uint32_t)RSF_E_DEEP_INVARIANT);
-    } else {
-      for (uint32_t b = 0; b < tc; b += U1 * kDeepThreads) {
-        uint4 x[U1];
 #pragma unroll
-        for (uint32_t u = 0; u < U1; ++u) {
-          const uint32_t i = b + u * kDeepThreads + tid;
-          x[u] = i < tc ? t[i] : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U1; ++u) {
-          const uint32_t i = b + u * kDeepThreads + tid;
-          put(i, i < tc, tlq_key(x[u].z & 0xFFFF, x[u].z >> 16, x[u].y));
-        }
+      for (uint32_t u = 0; u < U1; ++u) {
+        const uint32_t i = b + u * kDeepThreads + tid;
+        put(i, i < tc, tlq_key(x[u].z & 0xFFFF, x[u].z >> 16, x[u].y));
       }
     }
     an = wave_and_u64_blk(an);
@@ -1900,17 +2145,12 @@ __global__ void __launch_bounds__(kDeepThreads) check_stream_kernel(GCfg c, GSta
     const uint32_t m = min(s.tseal[l * 3 + q].x, tc);
     uint32_t kept_sealed = 0;
     for (uint32_t b = 0; b < tc; b += kChkU2 * kDeepThreads) {
-      // (the items move as they are: 8 B packed or 16 B; the keys come from pass 1)
+      // (the items move as they are; the keys come from pass 1)
       uint4 x[kChkU2];
 #pragma unroll
       for (uint32_t u = 0; u < kChkU2; ++u) {
         const uint32_t i = b + u * kDeepThreads + tid;
-        if (t8) {
-          const uint64_t v = i < tc ? t8[i] : 0ull;
-          x[u] = make_uint4((uint32_t)v, (uint32_t)(v >> 32), 0u, 0u);
-        } else {
-          x[u] = i < tc ? t[i] : make_uint4(0, 0, 0, 0);
-        }
+        x[u] = i < tc ? t[i] : make_uint4(0, 0, 0, 0);
       }
       uint64_t km[kChkU2];
 #pragma unroll
@@ -1932,11 +2172,7 @@ __global__ void __launch_bounds__(kDeepThreads) check_stream_kernel(GCfg c, GSta
         uint32_t before = 0;
 #pragma unroll
         for (uint32_t v = 0; v < kDeepWaves; ++v) before += v < w ? d.wcnt[u][v] : 0u;
-        if ((km[u] >> lane) & 1ull) {
-          const uint32_t at = base + before + mbcnt(km[u]);
-          if (t8) t8[at] = ((uint64_t)x[u].y << 32) | x[u].x;
-          else t[at] = x[u];
-        }
+        if ((km[u] >> lane) & 1ull) t[base + before + mbcnt(km[u])] = x[u];
 #pragma unroll
         for (uint32_t v = 0; v < kDeepWaves; ++v) base += d.wcnt[u][v];
       }
@@ -1966,15 +2202,7 @@ __global__ void __launch_bounds__(kDeepThreads) check_stream_kernel(GCfg c, GSta
       s.tseal[l * 3 + q] = ms ? make_uint4(ms, os.y, os.z, os.w) : kTSumEmpty;
     }
     __syncthreads();
-#if RSF_DEEP_PROF
-    const uint64_t ck4 = clock64();
-    pf[0] += ck1 - ck0;
-    pf[1] += ck2 - ck1;
-    pf[2] += ck3 - ck2;
-    pf[3] += ck4 - ck3;
-    pf[4] += n;
-    pc++;
-#endif
+    tally(n);
   }
 #if RSF_DEEP_PROF
   if (tid == 0) {
